@@ -12,8 +12,11 @@ is split over the ranks (reference DDP semantics: per-GPU batch = eff // gpus).
 
     python bench.py [--gpus N --steps K --warmup W]     (N > 1 via torch.distributed.run)
 
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for the roofline
-accounting.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the headline
+rate and ``ms_per_step``.  ``--dump-outputs DIR`` also writes what the last timed step computed
+(DIR/<name>.npy).  ``--full`` adds every other leg to that line: the per-kernel roofline, the
+configs[2] and F32 legs, the CPU baseline and the PSNR legs (each with its own ``--no-*`` switch).
+See DESIGN.md "Measurement" for the roofline accounting.
 """
 import argparse
 import json
@@ -49,7 +52,13 @@ def parse():
     ap.add_argument("--samples", type=int, default=128)
     ap.add_argument("--rd", type=int, default=1)
     ap.add_argument("--mode", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: per-kernel roofline (phase timing, "
+                         "reference GEMM), the configs[2] and F32 legs, the CPU baseline and the PSNR legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, rendered rays, gradient, updated "
+                         "parameters) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and PSNR legs")
     ap.add_argument("--no-gemm-peak", action="store_true", help="skip the hipBLASLt reference GEMM (profiling runs)")
     ap.add_argument("--pixbw", action="store_true",
                     help="BASELINE configs[2]: pixel-bandwidth model on (it_sample_size = --it-samples)")
@@ -724,6 +733,29 @@ def timed_steps(ts, a, world, dev, sync):
     return elapsed
 
 
+# What a caller of ``step()`` holds after it returns, per step class: dumped name -> attribute.  The
+# loss terms, the reduced gradient [MLP | background] and the parameters Adam left; the fused
+# TrainStep also keeps the rendered rays of its forward (PixbwTrainStep renders inside an autograd
+# graph it drops with the step, so its dump compares loss, gradient and parameters only).
+_TRAINED = (("loss", "loss"), ("grad", "gbuf"), ("params", "flat"), ("bkgd_param", "bkgd_orig"))
+STEP_OUTPUTS = {"TrainStep": _TRAINED + (("rgb", "rgb"), ("opacity", "opacity")),
+                "PixbwTrainStep": _TRAINED,
+                "StubStep": (("loss", "loss"), ("grad", "gbuf"))}
+
+
+def step_outputs(ts):
+    """The arrays of STEP_OUTPUTS for this step object; a missing attribute is an error."""
+    return {name: getattr(ts, attr) for name, attr in STEP_OUTPUTS[type(ts).__name__]}
+
+
+def dump_outputs(ts, path):
+    """--dump-outputs: one float32 DIR/<name>.npy per array of ``step_outputs`` (a few MB in all)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in step_outputs(ts).items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+
+
 def init_ranks(a, world, local, dist_mod=dist, cuda=torch.cuda):
     """One process per GPU: rank `local` binds device `local` and joins the process group over RCCL
     (backend "nccl", bound to that device); --dist-backend gloo rehearses N ranks on fewer GPUs
@@ -759,6 +791,8 @@ def main():
         dev = torch.device("cpu")
         ts = StubStep(a.rays, world)
         elapsed = timed_steps(ts, a, world, dev, lambda: None)
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(ts, a.dump_outputs)
         if rank == 0:
             print(json.dumps({"metric": metric_name(a), "value": round(a.rays * a.steps / elapsed, 1),
                               "unit": "rays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -781,6 +815,29 @@ def main():
     ms = elapsed / a.steps * 1e3
     rays_per_step = a.rays
     value = rays_per_step * a.steps / elapsed
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(ts, a.dump_outputs)
+    out = {
+        "metric": metric_name(a),
+        "value": round(value, 1), "unit": "rays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": a.mode, "data": "synthetic (chair-like raw events + camera poses, PyTorch default-init weights)",
+        "config": {"workload": f"chair synthetic, pixel-bandwidth {'on (it_sample_size=%d)' % a.it_samples if a.pixbw else 'off'}, "
+                               f"{a.rays} rays x {a.samples} samples, "
+                               f"mlp 8x256 rd={a.rd}, event prep+rays+fwd+bwd+allreduce+Adam",
+                   "rays_per_step": a.rays, "rays_per_rank": rays_per_rank, "samples_per_ray": a.samples,
+                   "events_per_step": a.rays // per_event,
+                   "parallelism": f"ray-dp{world}",
+                   "collective": (("rccl" if a.dist_backend == "nccl" else "gloo (shared-GPU rehearsal)")
+                                  if world > 1 else None)},
+        "loss": [round(x, 6) for x in loss],
+    }
+    if not a.full:  # the plain run ends here: the headline line, nothing measured beyond the timed steps
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     nat.timing_enable(True)
     if a.pixbw:  # autograd-chained step: per-kernel timing over whole steps, no phase split
@@ -871,25 +928,7 @@ def main():
                 except Exception as e:  # pragma: no cover - reported, not fatal
                     psnr_info = dict(psnr_info or {}, samples128={"error": repr(e)})
     if rank == 0:
-        out = {
-            "metric": metric_name(a),
-            "value": round(value, 1), "unit": "rays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": a.mode, "data": "synthetic (chair-like raw events + camera poses, PyTorch default-init weights)",
-            "config": {"workload": f"chair synthetic, pixel-bandwidth {'on (it_sample_size=%d)' % a.it_samples if a.pixbw else 'off'}, "
-                                   f"{a.rays} rays x {a.samples} samples, "
-                                   f"mlp 8x256 rd={a.rd}, event prep+rays+fwd+bwd+allreduce+Adam",
-                       "rays_per_step": a.rays, "rays_per_rank": rays_per_rank, "samples_per_ray": a.samples,
-                       "events_per_step": a.rays // per_event,
-                       "parallelism": f"ray-dp{world}",
-                       "collective": (("rccl" if a.dist_backend == "nccl" else "gloo (shared-GPU rehearsal)")
-                                      if world > 1 else None)},
-            "loss": [round(x, 6) for x in loss],
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "extra_legs": legs,
-            "psnr": psnr_info,
-        }
+        out.update(roofline=roofline, cpu_baseline=cpu, extra_legs=legs, psnr=psnr_info)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,6 +1,6 @@
 """Summarise rocprofv3 output of profiles/gpu_round.sh into committed evidence.
 
-    python profiles/pmc_summary.py gpurun_out <round tag>
+    python profiles/pmc_summary.py bench_out <round tag>      (gpu_round.sh's OUT folder)
 
 * profiles/pmc_traffic.json -- HBM bytes per launch of each render-path kernel
   from the separate `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` passes, corrected
@@ -81,7 +81,7 @@ def mfma_summary(out_dir, tag, n_simd=1024, prefix=""):
                   "valu_insts_per_mfma": round(c.get("SQ_INSTS_VALU", 0) / max(c.get("SQ_INSTS_MFMA", 1), 1), 2)}
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), f"{tag}_pmc_mfma.json"), "w") as f:
         json.dump({"source": f"rocprofv3 --pmc, two SQ passes ({tag}); see pmc_summary.mfma_summary",
-                   "command": "bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-gemm-peak", "kernels": res}, f,
+                   "command": "bench.py --steps 1 --warmup 1", "kernels": res}, f,
                   indent=1)
     return res
 
@@ -90,7 +90,7 @@ def roofline_check(out_dir, tag, prefix="", phase_reps=3):
     """roofline.frac reproduced from the rocprofv3 kernel trace of the SAME process that printed the
     bench line (``<prefix>prof/run_kernel_trace.csv`` + the JSON line in ``<prefix>prof.log``).
 
-    bench.py times the dominant kernel with HIP events during its phase-timing leg (PHASE_REPS
+    bench.py --full times the dominant kernel with HIP events during its phase-timing leg (PHASE_REPS
     steps after the timed region); those are the LAST ``launches_per_step x PHASE_REPS`` launches of
     that kernel in the trace.  Their rocprof mean, the mean over every launch (cold first steps
     included -- the r03 discrepancy), and the bench's HIP-event mean are written side by side with
@@ -138,7 +138,7 @@ def main(out_dir, tag, prefix=""):
                    "hbm_bytes_per_launch": rd + wr}
     res = {"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes ({tag}); "
                      "FETCH_SIZE x2 (gfx950 wide-read correction), KiB -> bytes",
-           "command": f"bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-gemm-peak ({f'profiles/gpu_{prefix[:-1]}.sh' if prefix else 'profiles/gpu_r02a.sh'})",
+           "command": f"bench.py --steps 1 --warmup 1 ({f'profiles/gpu_{prefix[:-1]}.sh' if prefix else 'profiles/gpu_round.sh'})",
            "workload": {"rays": 131072, "samples": 128, "mode": "bf16", "rd": 1},
            "kernels": kern}
     with open(os.path.join(here, "pmc_traffic.json"), "w") as f:
@@ -147,8 +147,9 @@ def main(out_dir, tag, prefix=""):
     with open(os.path.join(out_dir, prefix + "prof", "run_kernel_stats.csv")) as f:
         for r in csv.DictReader(f):
             rows.append(r)
-    # the traced command (PROF_CMD, set by the gpu script; the r02-r06fin3 scripts ran this default)
-    cmd = os.environ.get("PROF_CMD", "python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-gemm-peak")
+    # the traced command (PROF_CMD, set by the gpu script; the default is gpu_round.sh's: --full, because
+    # roofline_check reads the line's `roofline`, which only a --full run measures)
+    cmd = os.environ.get("PROF_CMD", "python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline")
     lines = [f"# rocprofv3 --kernel-trace --stats ({tag})", "",
              f"Command: `rocprofv3 --kernel-trace --stats --output-format csv -- {cmd}` ("
              + (f"profiles/gpu_{prefix[:-1]}.sh" if prefix else "profiles/gpu_r02a.sh, gpu_r02g.sh")

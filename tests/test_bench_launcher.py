@@ -11,6 +11,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 from conftest import ROOT
 
 
@@ -145,3 +148,96 @@ def test_gpus_defaults_to_world_size(monkeypatch):
     monkeypatch.delenv("WORLD_SIZE")
     a = bench.parse()
     assert a.gpus == 1 and a.psnr_steps == bench.PSNR_LEG["steps"]
+
+
+def test_full_is_off_by_default(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_stub_dumps_its_outputs(tmp_path):
+    p, lines = _run("--gpus", "1", "--dump-outputs", str(tmp_path / "out"))
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads(lines[-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "out")) == ["grad.npy", "loss.npy"]
+    loss = np.load(tmp_path / "out" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == (4,) and np.isfinite(loss).all()
+
+
+FULL_ONLY = ("roofline", "cpu_baseline", "extra_legs", "psnr")
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_outputs(tmp_path, monkeypatch, capsys):
+    """A plain run prints the headline line without any --full leg, runs exactly --steps timed steps
+    after --warmup, and --dump-outputs writes the last step's arrays as float32; a second run with
+    the same arguments starts from the same inputs and (fixed-order reductions) dumps the same bits."""
+    bench = _bench_module()
+    steps = []
+
+    def run(d, k):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--rays", "8192", "--steps", str(k), "--warmup", "1",
+                                          "--dump-outputs", str(d)])
+        bench.main()
+        return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+
+    real = bench.build_step
+
+    def counting(*a, **kw):
+        ts, per_event = real(*a, **kw)
+        inner = ts.step
+
+        def step():
+            steps.append(1)
+            return inner()
+        ts.step = step
+        return ts, per_event
+    monkeypatch.setattr(bench, "build_step", counting)
+    line = run(tmp_path / "a", 2)
+    assert len(steps) == 3 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["unit"] == "rays/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["metric"] == "train-step rays/sec at 8192 rays x 128 samples"
+    assert abs(line["value"] - 8192 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+    assert not any(k in line for k in FULL_ONLY)
+    run(tmp_path / "b", 2)
+    names = sorted(f for f in os.listdir(tmp_path / "a"))
+    assert names == ["bkgd_param.npy", "grad.npy", "loss.npy", "opacity.npy", "params.npy", "rgb.npy"]
+    assert names == sorted(n + ".npy" for n, _ in bench.STEP_OUTPUTS["TrainStep"])
+    total = 0
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and np.isfinite(x).all(), f
+        assert np.array_equal(x, y), f
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "rgb.npy").shape == (8192, 1)
+    assert np.allclose(np.load(tmp_path / "a" / "loss.npy")[:3], line["loss"], rtol=0, atol=1e-6)
+    # one more timed step moves the parameters: the dump is the LAST step's
+    run(tmp_path / "c", 3)
+    assert not np.array_equal(np.load(tmp_path / "c" / "params.npy"), np.load(tmp_path / "a" / "params.npy"))
+
+
+@pytest.mark.gpu
+def test_pixbw_run_dumps_its_outputs(tmp_path, monkeypatch, capsys):
+    """--pixbw --dump-outputs: the autograd-chained step holds no rendered rays after it returns, so
+    the dump is its loss, reduced gradient and updated parameters (16 events x 4 x S = 16)."""
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--pixbw", "--rays", "1024", "--steps", "2", "--warmup", "1",
+                                      "--dump-outputs", str(tmp_path)])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and not any(k in line for k in FULL_ONLY)
+    names = sorted(os.listdir(tmp_path))
+    assert names == ["bkgd_param.npy", "grad.npy", "loss.npy", "params.npy"]
+    assert names == sorted(n + ".npy" for n, _ in bench.STEP_OUTPUTS["PixbwTrainStep"])
+    for f in names:
+        x = np.load(tmp_path / f)
+        assert x.dtype == np.float32 and np.isfinite(x).all(), f
+    assert np.load(tmp_path / "grad.npy").shape[0] == np.load(tmp_path / "params.npy").shape[0] + 1
+    assert np.allclose(np.load(tmp_path / "loss.npy"), line["loss"], rtol=0, atol=1e-6)
