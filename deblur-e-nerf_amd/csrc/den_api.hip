@@ -89,22 +89,39 @@ struct TimedLaunch {
     g_timing_recs.push_back(r);
   }
 };
-#define DEN_TIMED(cls, s) TimedLaunch timed_##cls##_(cls, s)
+#define DEN_TIMED(cls, s) TimedLaunch timed_(cls, s)
 
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-
-
-struct WsLayout {
-  size_t act[NACT];
-  int64_t bstride[NACT + 1];  // bytes from one wave block of each activation (and D_ZB8) to the next
-  size_t sigma_dz;            // layer-major BF16: sigma's dz, one bf16 per sample (den_geom.h D_ZB8)
-  size_t rec, bkgd_partial, dw_partial, lr_partial, lr_stage1, pe_partial, total;
-  int splits;
-  int64_t per_split;
+struct WsRegion {
+  size_t off, bytes;  // bytes == 0: not allocated in this mode
+  const char* name;
 };
 
-constexpr int64_t DW_BLOCK_MAX = 9LL * 11 * 1024;  // floats per split, bound over the shapes (L5: MT 8, NT+1 11; Lb: MT 9, NT+1 9)
+struct WsLayout {
+  WsRegion rows;              // layer-major BF16 training: the block-major rows (den_geom.h SROW_BYTES)
+  WsRegion act[NACT];         // an activation inside `rows` has its offset there and bytes == 0
+  int64_t bstride[NACT + 1];  // bytes from one wave block of each activation (and D_ZB8) to the next
+  WsRegion sigma_dz;          // layer-major BF16: sigma's dz, one bf16 per sample (den_geom.h D_ZB8)
+  WsRegion rec, bkgd_partial, dw_partial, lr_partial, lr_stage1, pe_partial;
+  size_t total;
+  int splits;
+  int64_t per_split;
+  // the next region: `bytes` at the current end, which moves on to the next 256-byte boundary
+  WsRegion take(const char* name, size_t bytes) {
+    const WsRegion r{total, bytes, name};
+    total += align256(bytes);
+    return r;
+  }
+};
+
+// floats per split of dw_partial, a bound over the split-K shapes (launch_dw asserts it; the largest,
+// L5's, has 8 x 11 tiles)
+constexpr int64_t DW_BLOCK_MAX = dw_partial_floats(9, 10);
+// ... and per workgroup of the launches of hidden_grid() workgroups that share the region: the hidden
+// launches (Lb's 9 x 9 tiles) and the streamed weight gradients (launch_dwstream asserts it)
+constexpr int64_t DW_HIDDEN_MAX = hb_partial_floats(true);
+static_assert(hb_partial_floats(false) <= DW_HIDDEN_MAX);
 
 // persistent workgroups of the layer-major hidden backward: one per CU, at most one per wave block
 constexpr int LR_G1 = 1024;  // stage-1 rows of the fused Lr weight-gradient reduction (at most)
@@ -131,7 +148,6 @@ inline bool use_pe_fold(const den_render_desc* d) {
 WsLayout ws_layout(const den_render_desc* d) {
   WsLayout L{};
   const int64_t n = (int64_t)d->n_rays * d->n_samples;
-  size_t off = 0;
   const int tm = tm_of(d->mode), es = es_of(d->mode);
   const int64_t n_blocks = n / tm;
   for (int a = 0; a <= NACT; ++a)
@@ -146,32 +162,27 @@ WsLayout ws_layout(const den_render_desc* d) {
   // how each process's pages map to channels -- and at 6.2 TB/s within one row; the hidden launches
   // ran 4.88 / 4.73-4.98 / 4.64-4.73 ms for the three layouts.
   const bool rows = use_hidden_path(d) && d->train;
-  if (rows) {
-    for (int a = 0; a <= NACT; ++a) {
-      const int64_t o = srow_offset(a);
-      if (o < 0) continue;
-      L.act[a == D_ZB8 ? D_ZB : a] = off + (size_t)o;  // D_ZB's base is the dz_b slot (the 288-wide D_ZB unused)
-      L.bstride[a] = SROW_BYTES;
-    }
-    off += align256((size_t)n_blocks * (size_t)SROW_BYTES);
-    L.sigma_dz = off;
-    off += align256((size_t)n * 2);
+  L.rows = L.take("rows", rows ? (size_t)n_blocks * (size_t)SROW_BYTES : 0);
+  L.sigma_dz = L.take("sigma_dz", rows ? (size_t)n * 2 : 0);
+  for (int a = 0; rows && a <= NACT; ++a) {
+    const int64_t o = srow_offset(a);
+    if (o < 0) continue;
+    L.act[a == D_ZB8 ? D_ZB : a] = {L.rows.off + (size_t)o, 0, "rows"};  // D_ZB's base is the dz_b slot (the 288-wide D_ZB unused)
+    L.bstride[a] = SROW_BYTES;
   }
   for (int a = 0; a < NACT; ++a) {
     if (rows && (srow_offset(a) >= 0 || a == D_ZB)) continue;
-    L.act[a] = off;
     // pe: kept by the forward (read once by the streamed L0 / L5-pe weight gradient); ve: kept by the
     // F32 forward only (the BF16 head backward recomputes its tile in LDS; the sample-major BF16 path
     // writes it itself, enc_store_kernel)
     // dz_g: kept on chip by the BF16 head backward (render_head_bwd_kernel, the fused Lg weight
     // gradient) unless den_render_ray_grad will read it
     const bool enc = a == A_VE || (a == D_ZG && !d->ray_grad);
-    if (d->train && !(enc && use_hidden_path(d))) off += align256((size_t)n * act_width(d->mode, a) * es);
+    const bool kept = d->train && !(enc && use_hidden_path(d));
+    L.act[a] = L.take("act", kept ? (size_t)n * act_width(d->mode, a) * es : 0);
   }
-  L.rec = off;
-  if (d->train) off += align256((size_t)n * 16);
-  L.bkgd_partial = off;
-  off += align256((size_t)4 * d->n_rays * 4);
+  L.rec = L.take("rec", d->train ? (size_t)n * 16 : 0);
+  L.bkgd_partial = L.take("bkgd_partial", (size_t)4 * d->n_rays * 4);
   // weight-gradient split-K: >= 2048 samples per split, <= 256 splits
   int64_t splits = std::max<int64_t>(1, std::min<int64_t>(256, n / 2048));
   int64_t per = (n + splits - 1) / splits;
@@ -179,30 +190,27 @@ WsLayout ws_layout(const den_render_desc* d) {
   splits = (n + per - 1) / per;
   L.splits = (int)splits;
   L.per_split = per;
-  L.dw_partial = off;
-  // shared by the split-K GEMMs, the layer-major hidden backward (den_hidden.hip) and the streamed
-  // weight gradients (den_dwstream.hip, at most 9 x 9 tiles per workgroup)
-  const size_t hidden = (size_t)hidden_grid(n) * 9 * 9 * 1024;
-  if (d->train) off += align256(std::max((size_t)splits * DW_BLOCK_MAX, hidden) * 4);
+  // shared by the split-K GEMMs, the layer-major hidden backward (den_hidden.hip), the head's Lg
+  // partial (den_head_bwd.hip) and the streamed weight gradients (den_dwstream.hip)
+  const size_t dw_floats = std::max((size_t)splits * DW_BLOCK_MAX, (size_t)hidden_grid(n) * DW_HIDDEN_MAX);
+  L.dw_partial = L.take("dw_partial", d->train ? dw_floats * 4 : 0);
   // fused Lr weight gradient (render_bwd_kernel<1, 1>): one LR_PART-float partial per render
   // workgroup + the stage-1 rows of its reduction
-  L.lr_partial = off;
-  L.lr_stage1 = off;
-  if (d->train && use_hidden_path(d)) {
-    off += align256((size_t)(n / wg_samples(d->mode)) * LR_PART * 4);
-    L.lr_stage1 = off;
-    off += align256((size_t)LR_G1 * LR_PART * 4);
-  }
+  const bool lr = d->train && use_hidden_path(d);
+  L.lr_partial = L.take("lr_partial", lr ? (size_t)(n / wg_samples(d->mode)) * LR_PART * 4 : 0);
+  L.lr_stage1 = L.take("lr_stage1", lr ? (size_t)LR_G1 * LR_PART * 4 : 0);
   // the folded pe weight gradients' split-K partials (den_dwstream.hip's [wg][16][3] layout), written
   // by the L5 and L1 launches, reduced after both
-  L.pe_partial = off;
-  if (use_pe_fold(d)) off += align256((size_t)hidden_grid(n) * 16 * 3 * 1024 * 4);
-  L.total = off;
+  L.pe_partial = L.take("pe_partial", use_pe_fold(d) ? (size_t)hidden_grid(n) * HB_PE_PARTIAL_FLOATS * 4 : 0);
   return L;
 }
 
-// bytes from one wave block of activation `a` to the next
-inline int64_t block_bytes(const WsLayout& L, int mode, int a) { return L.bstride[a]; }
+// A launch of `count` workgroups (splits, rows), each with `floats` floats of region `r`, must fit it.
+int check_fits(const WsRegion& r, int64_t count, int64_t floats) {
+  if ((size_t)count * (size_t)floats * 4 <= r.bytes) return DEN_OK;
+  return fail(DEN_EINVAL, std::string("workspace region ") + r.name + ": " + std::to_string(count) + " x " +
+                              std::to_string(floats) + " floats do not fit its " + std::to_string(r.bytes) + " bytes");
+}
 
 int check_desc(const den_render_desc* d) {
   if (!d) return fail(DEN_EINVAL, "null desc");
@@ -249,54 +257,47 @@ RenderArgs<MODE> make_args(const den_render_desc* d, const den_render_io* io, co
   A.bias = io->bias_pk;
   A.bkgd = io->bkgd;
   char* ws = (char*)io->workspace;
-  for (int a = 0; a < NACT; ++a) A.act[a] = ws ? ws + L.act[a] : nullptr;
-  A.rec = ws ? (float*)(ws + L.rec) : nullptr;
-  A.bkgd_partial = ws ? (float*)(ws + L.bkgd_partial) : nullptr;
-  A.lr_partial = ws ? (float*)(ws + L.lr_partial) : nullptr;
+  for (int a = 0; a < NACT; ++a) A.act[a] = ws ? ws + L.act[a].off : nullptr;
+  A.rec = ws ? (float*)(ws + L.rec.off) : nullptr;
+  A.bkgd_partial = ws ? (float*)(ws + L.bkgd_partial.off) : nullptr;
+  A.lr_partial = ws ? (float*)(ws + L.lr_partial.off) : nullptr;
   A.out_rgb = io->out_rgb;
   A.out_opacity = io->out_opacity;
   A.out_depth = io->out_depth;
   A.density_act = d->density_activation;
   A.keep_dzg = d->ray_grad;
   for (int a = 0; a <= NACT; ++a) A.bstride[a] = L.bstride[a];
-  A.sigma_dz = ws ? ws + L.sigma_dz : nullptr;
+  A.sigma_dz = ws ? ws + L.sigma_dz.off : nullptr;
   return A;
 }
 
-// Split-K weight-gradient GEMM of one layer + its reduction into the flat gradient.
-// red_n1 < 0: columns [0, N1) are the first input segment; red_n1 = 0 maps every column to the
-// second segment at chain feature n1_feat (the pe columns of L5).  bias = 0 skips the bias.
-template <int MODE, int MT, int N1, int N2, int WN = 1>
-int launch_dw(const den_render_desc* d, const WsLayout& L, char* ws, int layer, int a_dz, int a_x1, int a_x2,
-              int n1_feat, float* grad, hipStream_t s, int m_off = 0, int red_n1 = -1, int bias = 1) {
-  DwArgs P{};
-  P.A = ws + L.act[a_dz];
-  P.a_tiles = act_width(MODE, a_dz) / tm_of(MODE);
-  P.a_t0 = m_off / tm_of(MODE);
-  P.B1 = ws + L.act[a_x1];
-  P.B2 = a_x2 >= 0 ? ws + L.act[a_x2] : nullptr;
-  P.n = (int64_t)d->n_rays * d->n_samples;
-  P.per_split = L.per_split;
-  P.partial = (float*)(ws + L.dw_partial);
-  {
-    DEN_TIMED(T_DW_GEMM, s);
-    hipLaunchKernelGGL((dw_gemm_kernel<MODE, MT, N1, N2, WN>), dim3(L.splits), dim3(64 * MT * WN), 0, s, P);
-  }
-  DEN_LAUNCHED();
+// The fields every weight-gradient reduction shares, with the split-K defaults: m_off = 0, split_stride
+// = 0 (the partials lie MT x (NT + 1) tiles apart) and first = 0.  n1: columns [0, n1) are the first
+// input segment, the rest the second at chain feature n1_feat (n1 = 0: all of them, the pe columns of
+// L5); bias = 0 skips the bias.  partial and splits are launch_reduce's.
+DwReduceArgs reduce_args(const den_render_desc* d, float* grad, int MT, int NT, int layer, int n1, int n1_feat,
+                         int bias) {
   DwReduceArgs R{};
-  R.partial = P.partial;
-  R.splits = L.splits;
   R.MT = MT;
-  R.NT = (N1 + N2) / 32;
-  R.m_off = m_off;
+  R.NT = NT;
   R.layer = layer;
-  R.mode = MODE;
+  R.mode = d->mode;
   R.rd = d->radiance_dim;
-  R.n1 = red_n1 < 0 ? N1 : red_n1;
+  R.n1 = n1;
   R.n1_feat = n1_feat;
   R.bias = bias;
   R.grad = grad;
-  const int64_t per = (int64_t)MT * (R.NT + 1) * 1024;
+  return R;
+}
+
+// The launch of dw_reduce_kernel: the sum over the `splits` partials of `region` into the gradient.
+int launch_reduce(DwReduceArgs R, const WsRegion& region, char* ws, int64_t splits, hipStream_t s) {
+  const int64_t per = dw_partial_floats(R.MT, R.NT);
+  // (a reduction of some row tiles of wider partials, split_stride apart, stays inside each of them)
+  int rc = check_fits(region, splits, R.split_stride > 0 ? R.split_stride : per);
+  if (rc != DEN_OK) return rc;
+  R.partial = (const float*)(ws + region.off);
+  R.splits = (int)splits;
   {
     DEN_TIMED(T_DW_REDUCE, s);
     hipLaunchKernelGGL(dw_reduce_kernel, dim3((unsigned)((per + DWR_EL - 1) / DWR_EL)), dim3(DWR_THREADS), 0, s, R);
@@ -305,24 +306,54 @@ int launch_dw(const den_render_desc* d, const WsLayout& L, char* ws, int layer, 
   return DEN_OK;
 }
 
+// Split-K weight-gradient GEMM of one layer + its reduction into the flat gradient.
+template <int MODE, int MT, int N1, int N2, int WN = 1>
+int launch_dw(const den_render_desc* d, const WsLayout& L, char* ws, int layer, int a_dz, int a_x1, int a_x2,
+              int n1_feat, float* grad, hipStream_t s, int m_off = 0) {
+  constexpr int NT = (N1 + N2) / 32;
+  static_assert(dw_partial_floats(MT, NT) <= DW_BLOCK_MAX, "ws_layout sizes dw_partial by DW_BLOCK_MAX per split");
+  int rc = check_fits(L.dw_partial, L.splits, dw_partial_floats(MT, NT));
+  if (rc != DEN_OK) return rc;
+  DwArgs P{};
+  P.A = ws + L.act[a_dz].off;
+  P.a_tiles = act_width(MODE, a_dz) / tm_of(MODE);
+  P.a_t0 = m_off / tm_of(MODE);
+  P.B1 = ws + L.act[a_x1].off;
+  P.B2 = a_x2 >= 0 ? ws + L.act[a_x2].off : nullptr;
+  P.n = (int64_t)d->n_rays * d->n_samples;
+  P.per_split = L.per_split;
+  P.partial = (float*)(ws + L.dw_partial.off);
+  {
+    DEN_TIMED(T_DW_GEMM, s);
+    hipLaunchKernelGGL((dw_gemm_kernel<MODE, MT, N1, N2, WN>), dim3(L.splits), dim3(64 * MT * WN), 0, s, P);
+  }
+  DEN_LAUNCHED();
+  DwReduceArgs R = reduce_args(d, grad, MT, NT, layer, N1, n1_feat, 1);
+  R.m_off = m_off;
+  return launch_reduce(R, L.dw_partial, ws, L.splits, s);
+}
+
 // One streamed weight-gradient launch (den_dwstream.hip) over the whole sample range.
 template <int MA, int MT, int NB, int NT, int NW, int DEPTH, int U = 1>
 int launch_dwstream(const den_render_desc* d, const WsLayout& L, char* ws, int a0, int a1, int b0, int b1,
                     hipStream_t s) {
+  static_assert(dws_partial_floats(MT, NT) <= DW_HIDDEN_MAX, "ws_layout sizes dw_partial by DW_HIDDEN_MAX per workgroup");
   const int64_t n = (int64_t)d->n_rays * d->n_samples;
+  const int64_t grid = hidden_grid(d);
+  int rc = check_fits(L.dw_partial, grid, dws_partial_floats(MT, NT));
+  if (rc != DEN_OK) return rc;
   DwStreamArgs P{};
-  P.a[0] = ws + L.act[a0];
-  P.a_bs[0] = block_bytes(L, DEN_MODE_BF16, a0);
-  P.a[1] = a1 >= 0 ? ws + L.act[a1] : nullptr;
-  P.a_bs[1] = a1 >= 0 ? block_bytes(L, DEN_MODE_BF16, a1) : 0;
-  P.b[0] = b0 >= 0 ? ws + L.act[b0] : nullptr;
-  P.b_bs[0] = b0 >= 0 ? block_bytes(L, DEN_MODE_BF16, b0) : 0;
-  P.b[1] = b1 >= 0 ? ws + L.act[b1] : nullptr;
-  P.b_bs[1] = b1 >= 0 ? block_bytes(L, DEN_MODE_BF16, b1) : 0;
-  P.partial = (float*)(ws + L.dw_partial);
+  P.a[0] = ws + L.act[a0].off;
+  P.a_bs[0] = L.bstride[a0];
+  P.a[1] = a1 >= 0 ? ws + L.act[a1].off : nullptr;
+  P.a_bs[1] = a1 >= 0 ? L.bstride[a1] : 0;
+  P.b[0] = b0 >= 0 ? ws + L.act[b0].off : nullptr;
+  P.b_bs[0] = b0 >= 0 ? L.bstride[b0] : 0;
+  P.b[1] = b1 >= 0 ? ws + L.act[b1].off : nullptr;
+  P.b_bs[1] = b1 >= 0 ? L.bstride[b1] : 0;
+  P.partial = (float*)(ws + L.dw_partial.off);
   static_assert(U == 1 || U == 2 || U == 4 || U == 8, "U divides the wave blocks (n is a multiple of 256)");
   P.n_blocks = n / 32 / U;
-  const int64_t grid = hidden_grid(d);
   P.per_wg = (P.n_blocks + grid - 1) / grid;
   {
     DEN_TIMED(T_DW_GEMM, s);
@@ -332,59 +363,34 @@ int launch_dwstream(const den_render_desc* d, const WsLayout& L, char* ws, int a
   return DEN_OK;
 }
 
-// Reduction of row tiles [mt0, mt0 + MT) of a streamed partial with NT_ALL column tiles into layer
-// `layer`'s gradient (red_n1 / n1_feat / bias as in launch_dw).
-int launch_dwstream_reduce(const den_render_desc* d, const WsLayout& L, char* ws, int MT_ALL, int NT_ALL, int mt0,
-                           int MT, int layer, int red_n1, int n1_feat, int bias, float* grad, hipStream_t s,
-                           int splits = -1, size_t region = (size_t)-1) {
-  DwReduceArgs R{};
-  R.partial = (float*)(ws + (region == (size_t)-1 ? L.dw_partial : region));
-  R.splits = splits > 0 ? splits : (int)hidden_grid(d);
-  R.MT = MT;
-  R.NT = NT_ALL;
-  R.m_off = 0;
-  R.layer = layer;
-  R.mode = DEN_MODE_BF16;
-  R.rd = d->radiance_dim;
-  R.n1 = red_n1;
-  R.n1_feat = n1_feat;
-  R.bias = bias;
-  R.grad = grad;
-  R.split_stride = (int64_t)MT_ALL * (NT_ALL + 1) * 1024;
-  R.first = (int64_t)mt0 * (NT_ALL + 1) * 1024;
-  const int64_t per = (int64_t)MT * (NT_ALL + 1) * 1024;
-  {
-    DEN_TIMED(T_DW_REDUCE, s);
-    hipLaunchKernelGGL(dw_reduce_kernel, dim3((unsigned)((per + DWR_EL - 1) / DWR_EL)), dim3(DWR_THREADS), 0, s, R);
-  }
-  DEN_LAUNCHED();
-  return DEN_OK;
+// Reduction of row tiles [mt0, mt0 + MT) of the `splits` per-workgroup partials in `region`, each of
+// MT_ALL x (NT_ALL + 1) tiles, into layer `layer`'s gradient (n1 / n1_feat / bias as in reduce_args).
+int launch_dwstream_reduce(const den_render_desc* d, const WsRegion& region, char* ws, int64_t splits, int MT_ALL,
+                           int NT_ALL, int mt0, int MT, int layer, int n1, int n1_feat, int bias, float* grad,
+                           hipStream_t s) {
+  DwReduceArgs R = reduce_args(d, grad, MT, NT_ALL, layer, n1, n1_feat, bias);
+  R.split_stride = dw_partial_floats(MT_ALL, NT_ALL);
+  R.first = dw_partial_floats(mt0, NT_ALL);
+  return launch_reduce(R, region, ws, splits, s);
 }
 
 // Reduction of the fused Lr weight-gradient partials (render_bwd_kernel<1, 1>) into the gradient.
 int launch_lr_reduce(const den_render_desc* d, const WsLayout& L, char* ws, float* grad, hipStream_t s, int64_t n_wg) {
   const int G1 = (int)std::min<int64_t>(LR_G1, n_wg);
-  DwReduceArgs R{};
-  R.MT = 1;
-  R.NT = 4;
-  R.m_off = 0;
-  R.layer = L_R;
-  R.mode = DEN_MODE_BF16;
-  R.rd = d->radiance_dim;
-  R.n1 = 128;
-  R.n1_feat = 0;
-  R.bias = 1;
-  R.grad = grad;
-  float* st1 = (float*)(ws + L.lr_stage1);
+  int rc;
+  if ((rc = check_fits(L.lr_partial, n_wg, LR_PART)) != DEN_OK) return rc;
+  if ((rc = check_fits(L.lr_stage1, G1, LR_PART)) != DEN_OK) return rc;
+  float* st1 = (float*)(ws + L.lr_stage1.off);
   {
     DEN_TIMED(T_DW_REDUCE, s);
-    hipLaunchKernelGGL(lr_reduce1_kernel, dim3((unsigned)G1), dim3(448), 0, s, (const float*)(ws + L.lr_partial), n_wg,
-                       G1, st1);
+    hipLaunchKernelGGL(lr_reduce1_kernel, dim3((unsigned)G1), dim3(448), 0, s,
+                       (const float*)(ws + L.lr_partial.off), n_wg, G1, st1);
   }
   DEN_LAUNCHED();
   {
     DEN_TIMED(T_DW_REDUCE, s);
-    hipLaunchKernelGGL(lr_reduce2_kernel, dim3(LR_PART - 1), dim3(256), 0, s, (const float*)st1, G1, R);
+    hipLaunchKernelGGL(lr_reduce2_kernel, dim3(LR_PART - 1), dim3(256), 0, s, (const float*)st1, G1,
+                       reduce_args(d, grad, 1, 4, L_R, 128, 0, 1));
   }
   DEN_LAUNCHED();
   return DEN_OK;
@@ -396,27 +402,30 @@ int launch_hidden(const den_render_desc* d, const den_render_io* io, const WsLay
                   hipStream_t s) {
   const int64_t n = (int64_t)d->n_rays * d->n_samples;
   const bool lb = l == 8;
+  // the pe fold: L5 adds dW_5's pe columns, L1 dW_0 (dz_0 then stays on chip)
+  const int pem = use_pe_fold(d) ? (l == 5 ? 1 : l == 1 ? 2 : 0) : 0;
+  const int64_t grid = hidden_grid(d);
+  int rc;
+  if ((rc = check_fits(L.dw_partial, grid, hb_partial_floats(lb))) != DEN_OK) return rc;
+  if (pem && (rc = check_fits(L.pe_partial, grid, HB_PE_PARTIAL_FLOATS)) != DEN_OK) return rc;
   HiddenArgs H{};
   H.w = (const char*)io->w_bwd + bwd_layer_offset(DEN_MODE_BF16, 10 - l);
-  H.dz_in = ws + L.act[lb ? D_ZB : D_Z0 + l];
-  H.s_in = ws + L.act[A_S0 + l - 1];
-  H.dz_out = ws + L.act[D_Z0 + l - 1];
-  H.partial = (float*)(ws + L.dw_partial);
+  H.dz_in = ws + L.act[lb ? D_ZB : D_Z0 + l].off;
+  H.s_in = ws + L.act[A_S0 + l - 1].off;
+  H.dz_out = ws + L.act[D_Z0 + l - 1].off;
+  H.partial = (float*)(ws + L.dw_partial.off);
   H.n_blocks = n / 32;
   H.bs_dz_in = L.bstride[lb ? D_ZB8 : D_Z0 + l];
   H.bs_s = L.bstride[A_S0 + l - 1];
   H.bs_dz_out = L.bstride[D_Z0 + l - 1];
-  H.sigma_dz = ws + L.sigma_dz;
-  // the pe fold: L5 adds dW_5's pe columns, L1 dW_0 (dz_0 then stays on chip)
-  const int pem = use_pe_fold(d) ? (l == 5 ? 1 : l == 1 ? 2 : 0) : 0;
-  H.pe = ws + L.act[A_PE];
+  H.sigma_dz = ws + L.sigma_dz.off;
+  H.pe = ws + L.act[A_PE].off;
   H.bs_pe = L.bstride[A_PE];
-  H.pe_partial = (float*)(ws + L.pe_partial);
+  H.pe_partial = (float*)(ws + L.pe_partial.off);
   H.pe_mt0 = l == 5 ? 8 : 0;
-  const int64_t grid = hidden_grid(d);
   H.per_wg = (H.n_blocks + grid - 1) / grid;
   {
-    TimedLaunch timed_(lb ? T_HIDDEN_LB : T_HIDDEN_BWD, s);
+    DEN_TIMED(lb ? T_HIDDEN_LB : T_HIDDEN_BWD, s);
     const dim3 g((unsigned)grid), t(HbCfg<false>::THREADS);
     if (lb)
       hipLaunchKernelGGL((hidden_bwd_kernel<true, 0>), g, dim3(HbCfg<true>::THREADS), 0, s, H);
@@ -428,25 +437,15 @@ int launch_hidden(const den_render_desc* d, const den_render_io* io, const WsLay
       hipLaunchKernelGGL((hidden_bwd_kernel<false, 0>), g, t, 0, s, H);
   }
   DEN_LAUNCHED();
-  if (lb) return launch_dwstream_reduce(d, L, ws, 9, 8, 0, 9, L_B, WIDTH, 0, 1, grad, s);
-  DwReduceArgs R{};
-  R.partial = H.partial;
-  R.splits = (int)grid;
-  R.MT = 8;
-  R.NT = 8;
-  R.m_off = 0;
-  R.layer = l;
-  R.mode = DEN_MODE_BF16;
-  R.rd = d->radiance_dim;
-  R.n1 = WIDTH;
-  R.n1_feat = 0;
-  R.bias = 1;
-  R.grad = grad;
-  const int64_t per = 8LL * 9 * 1024;
-  {
-    DEN_TIMED(T_DW_REDUCE, s);
-    hipLaunchKernelGGL(dw_reduce_kernel, dim3((unsigned)((per + DWR_EL - 1) / DWR_EL)), dim3(DWR_THREADS), 0, s, R);
-  }
+  if (lb) return launch_dwstream_reduce(d, L.dw_partial, ws, grid, 9, 8, 0, 9, L_B, WIDTH, 0, 1, grad, s);
+  return launch_reduce(reduce_args(d, grad, 8, 8, l, WIDTH, 0, 1), L.dw_partial, ws, grid, s);
+}
+
+// The background gradient: the sum of the rays' partials (written by the render backward).
+int launch_bkgd_reduce(const den_render_desc* d, const WsLayout& L, char* ws, float* grad_bkgd, hipStream_t s) {
+  if (!grad_bkgd) return DEN_OK;
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(d->radiance_dim), dim3(1024), 0, s, d->radiance_dim, d->n_rays,
+                     (const float*)(ws + L.bkgd_partial.off), grad_bkgd);
   DEN_LAUNCHED();
   return DEN_OK;
 }
@@ -507,20 +506,23 @@ int render_bwd_impl(const den_render_desc* d, const den_render_io* io, const den
         // head (compositing adjoint, Lr^T + dW_r, Lg^T + dW_g) sample-major and persistent, then Lb,
         // L7..L1 layer-major.  The Lg partial shares dw_partial with the hidden launches: reduced first.
         const int64_t items = n / wg_samples(MODE);
-        // one persistent workgroup per CU, as the forward; at most what the split-K partial region
-        // holds (4 x 10 tiles per workgroup; ws_layout sizes it for the hidden launches' 256 x 9 x 9,
-        // i.e. >= 518 head workgroups) and the Lr partials (one per item)
-        const int64_t dw_cap = (int64_t)(L.lr_partial - L.dw_partial) / (4 * 10 * 1024 * 4);
+        // one persistent workgroup per CU, as the forward, and at most one per item (lr_partial has a
+        // slot per item).  The Lg partials' share of dw_partial is a bound too, one that does not bind
+        // on a 256-CU device: sized for the hidden launches' 256 x 9 x 9 tiles, the region holds 518
+        // workgroups' 4 x 10.
+        const int64_t dw_cap = (int64_t)(L.dw_partial.bytes / (HD_LG_PARTIAL_FLOATS * 4));
         const int head_grid = (int)cap_grid(d, std::max<int64_t>(
             1, std::min<int64_t>({items, (int64_t)device_cu_count(s), dw_cap})));
+        if ((rc = check_fits(L.dw_partial, head_grid, HD_LG_PARTIAL_FLOATS)) != DEN_OK) return rc;
+        if ((rc = check_fits(L.lr_partial, head_grid, LR_PART)) != DEN_OK) return rc;
         {
           DEN_TIMED(T_RENDER_BWD, s);
           hipLaunchKernelGGL(render_head_bwd_kernel, dim3((unsigned)head_grid), dim3(512), 0, s, A,
-                             (float*)(ws + L.dw_partial));
+                             (float*)(ws + L.dw_partial.off));
         }
         DEN_LAUNCHED();
         if ((rc = launch_lr_reduce(d, L, ws, G, s, head_grid)) != DEN_OK) return rc;
-        if ((rc = launch_dwstream_reduce(d, L, ws, 4, 9, 0, 4, L_G, 256, WIDTH, 1, G, s, head_grid)) != DEN_OK)
+        if ((rc = launch_dwstream_reduce(d, L.dw_partial, ws, head_grid, 4, 9, 0, 4, L_G, 256, WIDTH, 1, G, s)) != DEN_OK)
           return rc;
         for (int l = 8; l >= 1; --l)
           if ((rc = launch_hidden(d, io, L, ws, l, G, s)) != DEN_OK) return rc;
@@ -538,18 +540,14 @@ int render_bwd_impl(const den_render_desc* d, const den_render_io* io, const den
     // L0's and L5's pe-column weight gradients: folded into the L1 / L5 launches (part 1 wrote their
     // partials), else streamed by one operand-sharing launch (den_dwstream.hip) over dz_0, dz_5 and pe
     const bool fold = use_pe_fold(d);
-    const size_t region = fold ? L.pe_partial : L.dw_partial;
+    const WsRegion& region = fold ? L.pe_partial : L.dw_partial;
+    const int64_t grid = hidden_grid(d);
     if (!fold && (rc = launch_dwstream<8, 16, 2, 2, DWS_NW1, 3, 1>(d, L, ws, D_Z0 + 0, D_Z0 + 5, A_PE, -1, s)) != DEN_OK)
       return rc;
-    if ((rc = launch_dwstream_reduce(d, L, ws, 16, 2, 0, 8, 0, 64, 0, 1, G, s, -1, region)) != DEN_OK) return rc;
-    if ((rc = launch_dwstream_reduce(d, L, ws, 16, 2, 8, 8, 5, 0, WIDTH, 0, G, s, -1, region)) != DEN_OK) return rc;
+    if ((rc = launch_dwstream_reduce(d, region, ws, grid, 16, 2, 0, 8, 0, 64, 0, 1, G, s)) != DEN_OK) return rc;
+    if ((rc = launch_dwstream_reduce(d, region, ws, grid, 16, 2, 8, 8, 5, 0, WIDTH, 0, G, s)) != DEN_OK) return rc;
     // (Lb's weight gradient comes from its hidden launch, Lr's and Lg's from render_head_bwd_kernel)
-    if (g->grad_bkgd) {
-      hipLaunchKernelGGL(sum_partials_kernel, dim3(d->radiance_dim), dim3(1024), 0, s, d->radiance_dim, d->n_rays,
-                         (const float*)(ws + L.bkgd_partial), g->grad_bkgd);
-      DEN_LAUNCHED();
-    }
-    return DEN_OK;
+    return launch_bkgd_reduce(d, L, ws, g->grad_bkgd, s);
   }
   if constexpr (MODE == DEN_MODE_BF16) {
     const int64_t nb = n / 32;
@@ -557,18 +555,13 @@ int render_bwd_impl(const den_render_desc* d, const den_render_io* io, const den
     DEN_LAUNCHED();
   }
   if ((rc = launch_dw<MODE, 8, 64, 0>(d, L, ws, 0, D_Z0 + 0, A_PE, -1, 0, G, s)) != DEN_OK) return rc;
-  if (hidden) {
-    // pe columns of L5 (the S4 columns and the bias come from the hidden launch of layer 5)
-    if ((rc = launch_dw<MODE, 8, 64, 0>(d, L, ws, 5, D_Z0 + 5, A_PE, -1, WIDTH, G, s, 0, 0, 0)) != DEN_OK) return rc;
-  } else {
-    if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 1, D_Z0 + 1, A_S0 + 0, -1, 0, G, s)) != DEN_OK) return rc;
-    if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 2, D_Z0 + 2, A_S0 + 1, -1, 0, G, s)) != DEN_OK) return rc;
-    if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 3, D_Z0 + 3, A_S0 + 2, -1, 0, G, s)) != DEN_OK) return rc;
-    if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 4, D_Z0 + 4, A_S0 + 3, -1, 0, G, s)) != DEN_OK) return rc;
-    if ((rc = launch_dw<MODE, 8, 256, 64>(d, L, ws, 5, D_Z0 + 5, A_S0 + 4, A_PE, WIDTH, G, s)) != DEN_OK) return rc;
-    if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 6, D_Z0 + 6, A_S0 + 5, -1, 0, G, s)) != DEN_OK) return rc;
-    if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 7, D_Z0 + 7, A_S0 + 6, -1, 0, G, s)) != DEN_OK) return rc;
-  }
+  if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 1, D_Z0 + 1, A_S0 + 0, -1, 0, G, s)) != DEN_OK) return rc;
+  if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 2, D_Z0 + 2, A_S0 + 1, -1, 0, G, s)) != DEN_OK) return rc;
+  if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 3, D_Z0 + 3, A_S0 + 2, -1, 0, G, s)) != DEN_OK) return rc;
+  if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 4, D_Z0 + 4, A_S0 + 3, -1, 0, G, s)) != DEN_OK) return rc;
+  if ((rc = launch_dw<MODE, 8, 256, 64>(d, L, ws, 5, D_Z0 + 5, A_S0 + 4, A_PE, WIDTH, G, s)) != DEN_OK) return rc;
+  if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 6, D_Z0 + 6, A_S0 + 5, -1, 0, G, s)) != DEN_OK) return rc;
+  if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, 7, D_Z0 + 7, A_S0 + 6, -1, 0, G, s)) != DEN_OK) return rc;
   // [bottleneck | sigma]: the 256 bottleneck rows, then the sigma tile (row 256) with 4 waves splitting
   // its 8 column tiles (one 9-wave launch would spill: 9 accumulator tiles at 3 waves per SIMD)
   if ((rc = launch_dw<MODE, 8, 256, 0>(d, L, ws, L_B, D_ZB, A_S0 + 7, -1, 0, G, s)) != DEN_OK) return rc;
@@ -576,12 +569,7 @@ int render_bwd_impl(const den_render_desc* d, const den_render_io* io, const den
   if ((rc = launch_dw<MODE, 4, 256, 32>(d, L, ws, L_G, D_ZG, A_BT, A_VE, WIDTH, G, s)) != DEN_OK) return rc;
   // rgb output (M = 32): 4 waves split the 4 column tiles
   if ((rc = launch_dw<MODE, 1, 128, 0, 4>(d, L, ws, L_R, D_ZR, A_G, -1, 0, G, s)) != DEN_OK) return rc;
-  if (g->grad_bkgd) {
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(d->radiance_dim), dim3(1024), 0, s, d->radiance_dim, d->n_rays,
-                       (const float*)(ws + L.bkgd_partial), g->grad_bkgd);
-    DEN_LAUNCHED();
-  }
-  return DEN_OK;
+  return launch_bkgd_reduce(d, L, ws, g->grad_bkgd, s);
 }
 
 }  // namespace
@@ -759,8 +747,8 @@ int den_render_ray_grad(const den_render_desc* d, const den_render_io* io, const
   G.t0 = io->t_starts;
   G.t1 = io->t_ends;
   G.per_sample = (float*)rg_workspace;
-  RayGradMlp M{params, ws + L.act[D_Z0 + 0], ws + L.act[D_Z0 + 5], ws + L.act[D_ZG],
-               block_bytes(L, d->mode, D_Z0 + 0), block_bytes(L, d->mode, D_Z0 + 5), block_bytes(L, d->mode, D_ZG),
+  RayGradMlp M{params, ws + L.act[D_Z0 + 0].off, ws + L.act[D_Z0 + 5].off, ws + L.act[D_ZG].off,
+               L.bstride[D_Z0 + 0], L.bstride[D_Z0 + 5], L.bstride[D_ZG],
                d->mode == DEN_MODE_F32 ? 1.0f : (float)KAPPA};
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)((n + RG_THREADS - 1) / RG_THREADS);

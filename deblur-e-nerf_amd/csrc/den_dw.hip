@@ -54,6 +54,10 @@ __device__ __forceinline__ int64_t dw_unit(int v, int nt, int tiles, int t0, int
 
 constexpr int DW_BK_MAX = 32;  // samples per LDS stage (16 for register-heavy shapes)
 
+// floats of one split's (one workgroup's) partial [MT][NT + 1][64][16]: MT x NT 32 x 32 tiles + the
+// ones tile of each row.  The host sizes and checks the workspace regions with it (ws_layout).
+DEN_HD constexpr int64_t dw_partial_floats(int MT, int NT) { return (int64_t)MT * (NT + 1) * 1024; }
+
 template <int MODE>
 DEN_HD constexpr int dw_pad_bytes(int W) {
   // BF16: choose the row pitch so that 4 consecutive rows start 16 banks apart
@@ -237,7 +241,7 @@ __device__ void dw_scatter(const DwReduceArgs& R, int64_t e, float s);
 constexpr int DWR_THREADS = DWR_EL * DWR_SG;
 
 __global__ __launch_bounds__(DWR_THREADS) void dw_reduce_kernel(DwReduceArgs R) {
-  const int64_t per = (int64_t)R.MT * (R.NT + 1) * 1024;
+  const int64_t per = dw_partial_floats(R.MT, R.NT);
   const int64_t stride = R.split_stride > 0 ? R.split_stride : per;
   const int el = threadIdx.x % DWR_EL, g = threadIdx.x / DWR_EL;
   const int64_t e = (int64_t)blockIdx.x * DWR_EL + el;

@@ -29,6 +29,8 @@ namespace den {
 // waves per workgroup (r02 / r03 A/B, profiles/r0{2,3}_*experiments.txt: 4 -> 16 waves took the
 // streamed launches from 13.0 to 10.8 ms per step)
 constexpr int DWS_NW1 = 16;
+// floats of one workgroup's partial [MT][NT + 1][64][16] (DwStreamArgs::partial)
+constexpr int64_t dws_partial_floats(int MT, int NT) { return dw_partial_floats(MT, NT); }
 
 struct DwStreamArgs {
   const char* a[2];     // dz tensors (wave-block major), row tiles [0, MA) from a[0], [MA, MT) from a[1]
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(64 * NW, 1) void dwstream_kernel(DwStreamArgs P) {
   }
   DEN_CLOCK_END(4);
   // partial of this workgroup: [mt][nt][lane][16], the bias in the ones-tile slot nt = NT
-  float* base = P.partial + (int64_t)blockIdx.x * MT * (NT + 1) * 1024;
+  float* base = P.partial + (int64_t)blockIdx.x * dws_partial_floats(MT, NT);
 #pragma unroll
   for (int j = 0; j < TPW; ++j) {
     const int t = wave + j * NW;

@@ -70,6 +70,9 @@ __device__ __forceinline__ void hd_dma_tile(const char* src, char* dst) {
 // lane: per ray o, d, jitter, d_rgb, d_opacity, d_depth = 12 floats, then bkgd) are DMA'd during
 // the current item's first Lg^T step; that step's successors' counted waits cover them.
 constexpr int HD_NRAY = 256;
+// floats of one workgroup's Lg partial [4][10][64][16] (lg_partial; the host sizes dw_partial's head
+// share with it, den_api.hip)
+constexpr int64_t HD_LG_PARTIAL_FLOATS = dw_partial_floats(4, 9);
 template <typename AT>
 __device__ __forceinline__ int hd_stage_adjoint(const AT& A, int64_t nx, int wave, char* rec_lds, float* nray) {
   int tid = threadIdx.x;
@@ -479,7 +482,8 @@ __global__ __launch_bounds__(512, 1) void render_head_bwd_kernel(RenderArgs<1> A
   }
   // ---- Lg partial [wg][mt][nt][lane][16], nt = 9 the bias (den_dwstream.hip's layout)
   constexpr int NT = 9;
-  float* base = lg_partial + (int64_t)blockIdx.x * 4 * (NT + 1) * 1024;
+  static_assert(HD_LG_PARTIAL_FLOATS == 4 * (NT + 1) * 1024, "the partial's 4 x (NT + 1) tiles");
+  float* base = lg_partial + (int64_t)blockIdx.x * HD_LG_PARTIAL_FLOATS;
   auto put = [&](int mt, int nt, const f32x16& acc) {
     float* o = base + ((int64_t)mt * (NT + 1) + nt) * 1024 + lane * 16;
 #pragma unroll

@@ -62,6 +62,11 @@ template <int PEM> constexpr int hb_wtl_k() {  // (LDS: L5 156 KiB, L1 152 KiB)
 // help); dz_l fragments read 4 k-steps ahead; the epilogue and the dW MFMAs kept in separate phases
 // (overlapping them, in compiler order or a pinned interleave, was 1-2 ms per step slower).
 constexpr int HB_GRID_MAX = 256;  // persistent workgroups (one per CU)
+// floats of one workgroup's split-K partial (HiddenArgs::partial: 8 x 8 tiles + the bias tiles, Lb a
+// ninth row for sigma) and of its folded pe partial (HiddenArgs::pe_partial, den_dwstream.hip's
+// [16][3] tiles): what the host sizes dw_partial / pe_partial with (ws_layout in den_api.hip)
+constexpr int64_t hb_partial_floats(bool lb) { return dw_partial_floats(lb ? 9 : 8, 8); }
+constexpr int64_t HB_PE_PARTIAL_FLOATS = dw_partial_floats(16, 2);
 constexpr int HB_PF_L = 4;        // dz_l fragments read ahead of the chain MFMAs
 constexpr int HB_PF_LB = 1;       // (Lb: registers, see HbCfg)
 #ifndef DEN_HB_DEPTH_L
@@ -538,6 +543,7 @@ __global__ __launch_bounds__(HbCfg<LB>::THREADS, 1) void hidden_bwd_kernel(Hidde
   // split-K partial of this workgroup (dw_gemm_kernel layout: [wg][mt][nt][lane][16]); the bias
   // goes where that layout's ones tile (nt = 8) keeps it: column 0 = lanes 0 and 32, row m in
   // register (m & 3) + 4 (m >> 3) of lane 32 ((m >> 2) & 1)
+  static_assert(hb_partial_floats(LB) == MTA * 9 * 1024, "the partial's [MTA][9] tiles per workgroup");
 #pragma unroll
   for (int t = 0; t < HB_RT; ++t) {
     const float bsum = db[t] + __shfl_xor(db[t], 32, 64);
@@ -574,6 +580,7 @@ __global__ __launch_bounds__(HbCfg<LB>::THREADS, 1) void hidden_bwd_kernel(Hidde
   if constexpr (PEM) {
     // pe partial ([wg][16][3] tiles): row tile pe_mt0 + w, pe column tiles 0, 1; L1's db_0 in the ones
     // tile (nt 2) where the hidden bias goes (above); L5's ones tile is never read (bias 0)
+    static_assert(HB_PE_PARTIAL_FLOATS == 16 * 3 * 1024, "the pe partial's [16][3] tiles per workgroup");
     float* o = P.pe_partial + (((int64_t)blockIdx.x * 16 + P.pe_mt0 + wave) * 3) * 1024;
 #pragma unroll
     for (int n = 0; n < 2; ++n)

@@ -177,9 +177,10 @@ const char* den_last_error(void);
 /* Kernel timing, for measurement only (bench.py's roofline).  While enabled,
  * every render-path launch is bracketed by two hipEvents recorded on its own
  * stream.  den_timing_collect waits for them and returns, per kernel class
- * (0 render_fwd_kernel, 1 render_bwd_kernel, 2 hidden_bwd_kernel,
- * 3 dw_gemm_kernel, 4 dw_reduce_kernel), the summed duration in ms and the
- * launch count since the last collect.  No reference counterpart. */
+ * (0 render_fwd_kernel, 1 render_bwd_kernel, 2 hidden_bwd_kernel (L7..L1),
+ * 3 dw_gemm_kernel, 4 dw_reduce_kernel, 5 hidden_bwd_lb_kernel: the Lb launch
+ * of hidden_bwd_kernel), the summed duration in ms and the launch count since
+ * the last collect.  No reference counterpart. */
 int den_timing_enable(int32_t on);
 int den_timing_collect(int32_t n_classes, double* total_ms, int64_t* launches);
 

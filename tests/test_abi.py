@@ -118,3 +118,49 @@ def test_training_workspace_fits_the_benchmark_shard():
     # the F32 parity layout keeps contiguous tensors (no rows): ~20 KB per sample
     desc = nat._desc(dict(cfg, mode=nat.MODE_F32), 4096, 128, True, True)
     assert L.den_render_workspace_bytes(ctypes.byref(desc)) / (4096 * 128) > 15000
+
+
+# den_render_workspace_bytes for rd 1, has_bkgd 1, points 0:
+# (mode, train, bwd_path, ray_grad, [(rays, samples), ...], bytes).  This pins the workspace layout
+# (ws_layout in den_api.hip): a deliberate layout change updates the table in the same commit.
+_ANY = (0, 1)
+WORKSPACE_BYTES = [
+    ("bf16", 1, (0,), (0,), [(4, 128), (8, 64), (2, 256)], 13_169_152),
+    ("bf16", 1, (0,), (1,), [(4, 128)], 10_154_496),
+    ("bf16", 1, (1,), _ANY, [(4, 128)], 10_461_440),
+    ("bf16", 1, (0,), (0,), [(96, 128)], 211_863_808),
+    ("bf16", 1, (0,), (1,), [(96, 128)], 164_677_888),
+    ("bf16", 1, (1,), (0,), [(96, 128)], 208_602_624),
+    ("bf16", 1, (0,), (0,), [(131072, 128)], 102_567_002_112),
+    ("bf16", 1, (0,), (1,), [(131072, 128)], 106_811_637_760),
+    ("bf16", 1, (1,), (0,), [(131072, 128)], 168_951_808_000),
+    ("f32", 1, _ANY, _ANY, [(4, 128)], 15_606_016),
+    ("f32", 1, _ANY, _ANY, [(96, 128)], 332_072_448),
+    ("f32", 1, _ANY, _ANY, [(131072, 128)], 337_529_274_368),
+    ("bf16", 0, _ANY, _ANY, [(4, 128)], 256),
+    ("bf16", 0, _ANY, _ANY, [(96, 128)], 1_536),
+    ("bf16", 0, _ANY, _ANY, [(131072, 128)], 2_097_152),
+    ("f32", 0, _ANY, _ANY, [(4, 128)], 256),
+    ("f32", 0, _ANY, _ANY, [(96, 128)], 1_536),
+    ("f32", 0, _ANY, _ANY, [(131072, 128)], 2_097_152),
+    ("f32", _ANY, _ANY, _ANY, [(2, 256)], 0),  # refused: 256 samples per ray is BF16 only
+]
+
+
+def test_render_workspace_bytes_table():
+    """The workspace size of every mode / path / shape class is the recorded one (host-only query)."""
+    import ctypes
+    nat, L = _lib()
+    bad = []
+    for mode, train, paths, ray_grads, shapes, want in WORKSPACE_BYTES:
+        for tr in (train if isinstance(train, tuple) else (train,)):
+            for bwd_path in paths:
+                for rg in ray_grads:
+                    for rays, samples in shapes:
+                        cfg = dict(mode=nat.mode_id(mode), rd=1, aabb=[-1.5] * 3 + [1.5] * 3, near=1.43, far=6.63,
+                                   bwd_path=bwd_path)
+                        desc = nat._desc(cfg, rays, samples, bool(tr), True, 0, bool(rg))
+                        got = L.den_render_workspace_bytes(ctypes.byref(desc))
+                        if got != want:
+                            bad.append((mode, tr, bwd_path, rg, rays, samples, got, want))
+    assert not bad, bad

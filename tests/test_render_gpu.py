@@ -179,6 +179,50 @@ def test_render_bf16_many_blocks_matches_oracle():
     assert worst <= 2e-2  # measured (r02): 6.9e-3
 
 
+@pytest.mark.parametrize("mode,ray_grad,bwd_path", [("bf16", 0, 0), ("bf16", 1, 0), ("bf16", 0, 1), ("f32", 0, 0)],
+                         ids=["bf16-fold", "bf16-streamed", "bf16-sample-major", "f32"])
+def test_render_bwd_parts_equal_whole_backward(mode, ray_grad, bwd_path):
+    """den_render_bwd_part(1) then (2) launch the kernels of one den_render_bwd in the same order on
+    the same stream: grad_params and grad_bkgd are bit-equal.  96 rays x 128 samples = 384 wave blocks
+    over 256 persistent workgroups (ragged per_wg, some workgroups empty).  The ABI is driven directly;
+    each backward gets its own forward (the layer-major path writes dz over S in place)."""
+    import ctypes
+    nat = _nat()
+    L = nat.lib()
+    rd, R, S = 3, 96, 128
+    o, d, u = (t.to(DEV).contiguous() for t in synthetic_rays(R, seed=41))
+    flat = flat_from_params(onerf.build_params(rd, 1), rd).to(DEV)
+    packed = nat.PackedWeights(mode, rd, DEV)
+    packed.pack(flat)
+    bk = torch.tensor([0.9, 0.8, 0.7], device=DEV)
+    desc = nat._desc(dict(_cfg(mode, rd), bwd_path=bwd_path), R, S, True, True, ray_grad=bool(ray_grad))
+    ws = torch.empty(nat.render_workspace_bytes(desc), dtype=torch.uint8, device=DEV)
+    out = torch.empty(R, rd, device=DEV), torch.empty(R, device=DEV), torch.empty(R, device=DEV)
+    io = nat.RenderIO(nat._ptr(o), nat._ptr(d), nat._ptr(u), nat._ptr(packed.fwd), nat._ptr(packed.bwd),
+                      nat._ptr(packed.bias), nat._ptr(bk), nat._ptr(ws), *(nat._ptr(t) for t in out), None, None, None)
+    gen = torch.Generator().manual_seed(42)
+    d_rgb, d_op = torch.randn(R, rd, generator=gen).to(DEV), torch.randn(R, generator=gen).to(DEV)
+    st = nat._stream(torch.device(DEV))
+
+    def backward(parts):
+        gp, gb = torch.zeros(nat.param_count(rd), device=DEV), torch.zeros(rd, device=DEV)
+        gr = nat.RenderGrad(nat._ptr(d_rgb), nat._ptr(d_op), None, nat._ptr(gp), nat._ptr(gb))
+        nat._check(L.den_render_fwd(ctypes.byref(desc), ctypes.byref(io), st))
+        if parts:
+            for part in (1, 2):
+                nat._check(L.den_render_bwd_part(ctypes.byref(desc), ctypes.byref(io), ctypes.byref(gr), part, st))
+        else:
+            nat._check(L.den_render_bwd(ctypes.byref(desc), ctypes.byref(io), ctypes.byref(gr), st))
+        torch.cuda.synchronize()
+        return gp, gb
+
+    gp, gb = backward(parts=False)
+    gp2, gb2 = backward(parts=True)
+    assert torch.isfinite(gp).all() and float(gp.abs().max()) > 0 and float(gb.abs().max()) > 0
+    assert torch.equal(gp2, gp)
+    assert torch.equal(gb2, gb)
+
+
 def test_render_rejects_bad_shapes():
     nat = _nat()
     flat = torch.zeros(nat.param_count(3), device=DEV)
